@@ -2,6 +2,7 @@
 """Headline benchmark: Ed25519 scalar-mults/sec on MI355X (BASELINE.json `metric`).
 
   python bench.py --gpus N --steps K --warmup W [--mode ranks|group] [--workload mul|mul_enc|mul_base|sign|verify] [--n ITEMS_PER_GPU]
+                  [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch that is already resident in HBM:
   mul       2^20 variable-base mults, random scalars + random points   (BASELINE configs[1], default, the line's `value`)
@@ -80,6 +81,8 @@ PEAK_MAD_NOMINAL = 1024 * 64 / 4 * 2.4e9
 HBM_PEAK_GBS = 8000.0
 DEFAULT_N = {"mul": 1 << 20, "mul_enc": 1 << 20, "mul_base": 1 << 20, "sign": 1 << 18, "verify": 1 << 20}
 PROFILE_ROUNDS = ("r06", "r05", "r04", "r03", "r02", "r01")
+DUMP_LIMIT_BYTES = 60_000_000          # --dump-outputs: all files of one dump together stay below 64 MB
+DUMP_SAMPLE_SEED = 7
 OPTION_KEYS = ("device.cus", "coop.max_items", "coop.base_max_items", "coop.ladder_max_items", "ladder.skip_canonical", "ladder.pair_max_items")      # (kernel variants are not options of the product library)
 
 
@@ -273,6 +276,37 @@ def time_workload(w, eng, rt, steps, warmup, barrier):
     w["launches"] = eng.profile_read(10 * steps)
     eng.profile_begin(0)
     return elapsed
+
+
+def output_arrays(w):
+    """what a caller of the workload's step receives: name -> device tensor, one row per item"""
+    wl = w["wl"]
+    if wl == "sign":
+        return {"signatures": w["out"]}
+    if wl == "verify":
+        return {"verdicts": w["out"]}
+    outs = {"encodings": w["out"]}
+    if wl == "mul_enc":
+        outs["ok"] = w["ok"]
+    return outs
+
+
+def dump_outputs(dirname, arrays, n):
+    """--dump-outputs: the arrays as DIR/<name>.npy in float32 (byte values are exact in it) and DIR/rows.npy (float64), the items written.
+    All n rows when everything fits in DUMP_LIMIT_BYTES, otherwise a sample of rows drawn with a fixed seed: the same rows in every run of the
+    same size, so two builds can be compared output for output"""
+    import numpy as np
+    import torch
+    row_bytes = 8 + sum(4 * (a.numel() // n) for a in arrays.values())
+    m = min(n, DUMP_LIMIT_BYTES // row_bytes)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, m, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    files = []
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a[torch.from_numpy(rows).to(a.device)].cpu().numpy().astype(np.float32))
+        files.append(name + ".npy")
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    return {"dir": dirname, "files": files + ["rows.npy"], "rows": int(m), "of_items": n, "dtype": "float32"}
 
 
 def kernel_clock(w, eng, rt, steps=3, warm=10):
@@ -844,6 +878,7 @@ def run_ranks(args):
     w = setup_workload(wl, n, eng, inp, rt, args.keyed)
     gen_s = time.time() - t0
     elapsed = time_workload(w, eng, rt, args.steps, args.warmup, barrier)
+    dumped = dump_outputs(args.dump_outputs, output_arrays(w), n) if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -888,6 +923,8 @@ def run_ranks(args):
         line.update({"input_gen_s": round(gen_s, 2), "ranks_seen": len(idents), "dist_backend": backend, "devices": idents,
                      "table_identical_on_all_ranks": len({d["table_sha256_16"] for d in idents}) == 1,
                      "launched_by": "self-spawned ranks" if os.environ.get("KYB_BENCH_SPAWNED") else ("external launcher" if world > 1 else "single process")})
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
         if args.standin:
             line.update({"metric": "STANDIN plumbing run (no GPU, no arithmetic): NOT a measurement", "data": "none (stand-in engine)", "roofline": None, "cpu_baseline": None,
                          "standin_calls": eng.calls})
@@ -1007,6 +1044,9 @@ def run_group(args):
     elapsed = time.perf_counter() - t_start
     launches = engs[0].profile_read(10 * args.steps)
     engs[0].profile_begin(0)
+    dumped = None
+    if args.dump_outputs:                        # rank 0's shard, as in ranks mode
+        dumped = dump_outputs(args.dump_outputs, output_arrays({"wl": wl, "out": out[0], "ok": ok[0] if ok else None}), n)
 
     orc = oracle_lib.Oracle()
     threads = max(1, min(len(os.sched_getaffinity(0)), 16))
@@ -1033,6 +1073,8 @@ def run_group(args):
                  "launched_by": "one process, kyb_group (one context and stream per GPU, launches queued by one thread)",
                  "rank0_kernels_ms_per_step": {k_: round(sum(v_) / args.steps, 4) for k_, v_ in per_kernel.items()},
                  "roofline": None, "cpu_baseline": None, "parity_checked_items": checked})
+    if dumped is not None:
+        line["outputs_dumped"] = dumped
     print(json.dumps(line), flush=True)
     grp.close()
 
@@ -1056,15 +1098,16 @@ def main():
     ap.add_argument("--only", action="store_true", help="time the primary workload only (no `workloads` object)")
     ap.add_argument("--check", type=int, default=16384, help="items verified against the oracle after timing (per workload)")
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value (kernel variant), repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the primary workload's last step "
+                    "returned (rank 0) as DIR/<name>.npy in float32, a fixed seeded row sample when the whole would exceed 64 MB")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)     # tests: real engines, gloo instead of RCCL
     ap.add_argument("--same-device", action="store_true", help=argparse.SUPPRESS)                           # tests: every rank on GPU 0
     ap.add_argument("--standin", action="store_true", help=argparse.SUPPRESS)      # tests only: CPU stand-in engine over gloo, prints a line marked as no measurement
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
-    # concurrent small calls want more hardware queues than the runtime's default of 4; the variable is read when the HIP runtime starts
-    # and belongs to the host program (the library never sets it): here, before anything initialises HIP
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.mode == "group":
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:

@@ -27,9 +27,9 @@
  *              used slot is recycled after its last launch); their launch bookkeeping is serialised per context.
  *              kyb_set_option / kyb_profile_* are safe against concurrent launches.
  *              Concurrent small calls of several contexts need hardware queues: the ROCm runtime maps all streams of a process onto
- *              GPU_MAX_HW_QUEUES queues (default 4).  The variable is read when the HIP runtime starts and belongs to the host
- *              program: this library never touches the environment; a host that issues one-item calls from many threads sets
- *              GPU_MAX_HW_QUEUES=16 before its first HIP call (16 threads: 16k -> 72k variable-base calls/s).
+ *              GPU_MAX_HW_QUEUES queues.  The variable is read when the HIP runtime starts and belongs to the host program and
+ *              the machine it runs on: this library never touches the environment, and one-item calls of many threads overlap
+ *              only as far as those queues allow.
  *   timing     The instruction stream, the LDS / memory addresses and the launch geometry of every kernel are independent of scalar
  *              VALUES, with documented exceptions, each a shape chosen from a PUBLIC property:
  *                ladder.skip_canonical (default 1): a launch whose scalars are ALL below 2^252 walks 252 bits instead of 256 — "is

@@ -116,8 +116,8 @@ fn table_image() -> &'static [u8] {
 
 /// Host-pointer calls of ONE context are serialised (its staging buffers and streams are one set), so every thread that touches a
 /// `Point` gets a context of its own on first use: N threads then run N small calls on the GPU at the same time
-/// (`profiles/r02/concurrent_small_calls.log`: 16 threads, 175,000 `mul(s, None)` per second; start the process with
-/// GPU_MAX_HW_QUEUES=16 for that — the library leaves the environment alone).  Options belong to a context.
+/// (`profiles/r02/concurrent_small_calls.log`: 16 threads, 175,000 `mul(s, None)` per second with 16 hardware queues; the queue
+/// count is the host's setting — the library leaves the environment alone).  Options belong to a context.
 struct ThreadCtx(*mut kyb_ctx);
 impl ThreadCtx {
     fn new() -> Self {

@@ -12,6 +12,11 @@ What is copied is DATA the reference's own tests hold for this path (SURVEY.md Â
         weak_keys      src/group/edwards25519/constants.rs:3744-3775
     plus quirk vectors whose expected outputs come from the C oracle and are cross-checked against
     oracle/bigint_model.py before being written (no reference test covers them; SURVEY.md Â§8c).
+  * reference_constants.json â€” the curve constants of src/group/edwards25519/constants.rs as numbers, limbs as written there
+    (D, D2, SQRT_M1, BASEEXT, the 256 entries of BASE, PRIME / PRIME_ORDER); tests/test_constants_vs_reference.py compares the
+    constants this repository derives with them.  `make_golden.py constants` writes this file alone.
+  * reference_point_impls.json â€” the `impl ... for Point` blocks of src/group/edwards25519/point.rs: trait, line and method NAMES
+    (tools/check_rust_shim.py part 1 where the reference tree is absent).  `make_golden.py impls` writes this file alone.
         embed          Point::embed / Point::pick (point.rs:90-92, 106-167) over replayed key streams: accepted candidate, blocks
                        consumed and the reason every earlier candidate was rejected (C oracle == big-int model, as above)
 """
@@ -202,5 +207,51 @@ def embed_vectors(orc, M, out):
     return vecs
 
 
+def constants_fixture():
+    """reference_constants.json: the literals of constants.rs as numbers (field elements as the reference's ten signed limbs)"""
+    src = open(os.path.join(REF, "src/group/edwards25519/constants.rs")).read()
+
+    def ints(txt):
+        return [int(x) for x in re.findall(r"-?\d+", txt)]
+
+    out = {"field_elements": {}}
+    for name in ("D", "D2", "SQRT_M1"):
+        m = re.search(r"pub const %s: FieldElement = \[(.*?)\];" % name, src, flags=re.S)
+        out["field_elements"][name] = ints(m.group(1))
+    m = re.search(r"pub const BASEEXT: ExtendedGroupElement = ExtendedGroupElement \{(.*?)\n\};", src, flags=re.S)
+    coords = re.findall(r"([xyzt]): \[(.*?)\]", m.group(1), flags=re.S)
+    out["baseext"] = {k: ints(v) for k, v in coords}
+    body = src[src.index("pub const BASE:"):src.index("pub const WEAK_KEYS")]
+    ents = re.findall(r"PreComputedGroupElement \{\s*y_plus_x: \[(.*?)\],\s*y_minus_x: \[(.*?)\],\s*xy2d: \[(.*?)\],\s*\}", body, flags=re.S)
+    assert len(ents) == 256 and all(len(ints(c)) == 10 for e in ents for c in e)
+    out["base"] = [[ints(c) for c in e] for e in ents]
+    for key, dec in (("prime", "57896044618658097711785492504343953926634992332820282019728792003956564819949"),
+                     ("prime_order", "7237005577332262213973186563042994240857116359379907606001950938285454250989")):
+        assert dec in src, key
+        out[key] = dec
+    with open(os.path.join(HERE, "reference_constants.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+
+
+def point_impls_fixture():
+    """reference_point_impls.json: which impl blocks of Point the reference has and the names of their methods"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_rust_shim as chk
+    blocks = chk.impl_blocks(open(os.path.join(REF, "src/group/edwards25519/point.rs")).read())
+    rows = [dict(trait=t, type=typ, line=line, fns=sorted(fns)) for (t, typ), (line, fns) in sorted(blocks.items(), key=lambda kv: kv[1][0]) if typ == "Point"]
+    assert rows
+    with open(os.path.join(HERE, "reference_point_impls.json"), "w") as f:
+        json.dump(rows, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["constants"]:
+        constants_fixture()
+    elif sys.argv[1:] == ["impls"]:
+        point_impls_fixture()
+    else:
+        main()
+        constants_fixture()
+        point_impls_fixture()

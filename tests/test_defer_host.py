@@ -4,6 +4,8 @@ chains counted, stale handles, four threads on one arena.  tests/hostcheck/defer
 import os
 import subprocess
 
+from sanitizer_run import sanitized
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -14,7 +16,7 @@ def test_deferred_evaluator_on_the_cpu_under_sanitizers(oracle):
     orc_dir = os.path.join(ROOT, "oracle", "_build")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-o", out, src, "-L", orc_dir, "-loracle", f"-Wl,-rpath,{orc_dir}", "-lpthread"])
-    r = subprocess.run([out], capture_output=True, text=True, timeout=900, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    r = subprocess.run(sanitized([out]), capture_output=True, text=True, timeout=900, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     print(r.stdout[-3000:], r.stderr[-3000:])
     assert r.returncode == 0 and r.stdout.strip().splitlines()[-1].startswith("OK")
 
@@ -27,6 +29,6 @@ def test_deferred_evaluator_under_thread_sanitizer(oracle):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     orc_dir = os.path.join(ROOT, "oracle", "_build")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unused-function", "-fsanitize=thread", "-o", out, src, "-L", orc_dir, "-loracle", f"-Wl,-rpath,{orc_dir}", "-lpthread"])
-    r = subprocess.run([out], capture_output=True, text=True, timeout=900)
+    r = subprocess.run(sanitized([out]), capture_output=True, text=True, timeout=900)
     print(r.stdout[-2000:], r.stderr[-3000:])
     assert r.returncode == 0 and "WARNING: ThreadSanitizer" not in r.stderr and r.stdout.strip().splitlines()[-1].startswith("OK")

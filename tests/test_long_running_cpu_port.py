@@ -6,12 +6,13 @@ KYB_E_STALE, abort.  The GPU run at n = 64, t = 43 past the real window of 2^18 
 import json
 import subprocess
 
+from sanitizer_run import sanitized
 from test_gpu_vss_round import build
 
 
 def _run(args, timeout=600):
     # (under AddressSanitizer + UBSan: the C++ mirror and the product's defer.inc — window moves, kept values, leaves taken back in)
-    return subprocess.run([build("test_long_running", cpu_defer=True, sanitize=True)] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
+    return subprocess.run(sanitized([build("test_long_running", cpu_defer=True, sanitize=True)] + [str(a) for a in args]), capture_output=True, text=True, timeout=timeout)
 
 
 def test_three_hundred_rounds_through_a_small_window(oracle):

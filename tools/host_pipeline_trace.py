@@ -7,7 +7,6 @@ and, without the profiler, the wall time per call."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
 import kyber_rs_amd
 
