@@ -49,10 +49,14 @@
  *   secrets    host-pointer calls that take secret scalars (kyb_mul_base_batch, kyb_mul_batch, the signing calls, kyb_pripoly_eval_batch)
  *              clear, before they return and on every error path, the copies of the secret INPUTS the engine made — page-locked zero-copy
  *              buffer, device staging, bounce ring — and kyb_mul_batch (whose result s*P is a Diffie-Hellman shared secret) also the
- *              copies of its OUTPUTS in the zero-copy buffer and the device staging.  Not cleared per call: the per-stream device scratch
- *              (projective staging records; overwritten by the next call on the stream, wiped when the context or the stream slot is
- *              released) and, for pageable callers of calls of 2^16 items and more, the page-locked landing area of the results (buffers
- *              from kyb_host_alloc bypass it).  Device-pointer calls work on the caller's own buffers and leave only the scratch.
+ *              copies of its OUTPUTS in the zero-copy buffer and the device staging.  After a call with secret inputs the per-stream
+ *              device scratch holds at most that call's RESULTS — the public s*B of kyb_mul_base_batch, R and A of signing, the s*P of
+ *              kyb_mul_batch (overwritten by the next call on the stream, wiped when the context or the stream slot is released); the
+ *              intermediates derived from the secrets — partial points of the fixed base, pieces of a variable-base product, segments
+ *              of a secret polynomial, expanded EdDSA keys and nonces — are cleared by the kernels that read them or before the call
+ *              returns, on error paths too.  Not cleared per call: for pageable callers of calls of 2^16 items and more, the page-locked
+ *              landing area of the results (buffers from kyb_host_alloc bypass it).  Device-pointer calls work on the caller's own
+ *              buffers and leave the same in the scratch as host-pointer calls.
  *
  * Two flavours of every batch call:
  *   kyb_xxx_batch      host pointers; H2D copy, kernel, D2H copy, synchronous.

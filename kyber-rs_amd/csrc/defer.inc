@@ -804,8 +804,11 @@ int kyb_defer_equal(uint64_t ha, uint64_t hb, uint8_t* eq) {
   ENTER_HOST();
   if (!eq) return fail(KYB_E_BAD_ARG, "null argument");
   if (ha == 0 || hb == 0) return fail(KYB_E_BAD_ARG, "deferred point: null handle");
+  // the stack copies below may be Diffie-Hellman shared secrets: cleared on every return path, as drecord's Vals
+  struct Copies { int32_t xa[40], xb[40]; uint8_t ea[32], eb[32]; ~Copies() { explicit_bzero(this, sizeof(*this)); } };
   if (arena_id_of(ha) != arena_id_of(hb)) {                 // points of two arenas: their limbs, then the ordinary comparison
-    int32_t xa[40], xb[40];
+    Copies cp;
+    int32_t *xa = cp.xa, *xb = cp.xb;
     int rc = dvalue(g, ha, xa, nullptr); if (rc) return rc;
     rc = dvalue(g, hb, xb, nullptr); if (rc) return rc;
     return kyb_equal_batch(xa, xb, 1, eq);
@@ -821,8 +824,9 @@ int kyb_defer_equal(uint64_t ha, uint64_t hb, uint8_t* eq) {
   std::lock_guard<std::mutex> lk(A.mu);
   const uint64_t a = seq_of(ha), b = seq_of(hb);
   if ((a != 0 && a < A.first_id) || (b != 0 && b < A.first_id)) {      // one of them lives in the table of kept values: limbs (evaluating the other if need be), then the ordinary comparison
-    int32_t xa[40], xb[40];
-    uint8_t ea[32], eb[32];
+    Copies cp;
+    int32_t *xa = cp.xa, *xb = cp.xb;
+    uint8_t *ea = cp.ea, *eb = cp.eb;
     auto fetch = [&](uint64_t q, int32_t* x, uint8_t* e, bool* has_enc) -> int {
       if (q < A.first_id) {
         DeferArena::Kept* k = A.kept_find(q);

@@ -1595,7 +1595,14 @@ int launch_pripoly_eval(Ctx& g, const uint8_t* coeffs, size_t m, size_t t, const
   if (segs < 1) segs = 1;
   if (segs > 1) { int rc = ensure_enc(g, r, 32 * evals * segs + 256); if (rc) return rc; }
   ProfScope ps(g, st, KID_PRIPOLY_EVAL);
-  LAUNCHCK(launch::pripoly_eval(st, coeffs, m, t, indices, k, (uint32_t)segs, static_cast<uint8_t*>(r->enc), out));
+  uint8_t* part = static_cast<uint8_t*>(r->enc);
+  LAUNCHCK(launch::pripoly_eval_part(st, coeffs, m, t, indices, k, (uint32_t)segs, part, out));
+  if (segs == 1) return KYB_OK;
+  // the partial values are secret: when the sum that clears them cannot be queued, they are cleared here
+  bool summed = false;
+  auto wipe = on_scope_exit([&] { if (!summed) (void)hipMemsetAsync(part, 0, 32 * evals * segs, st); });
+  LAUNCHCK(launch::pripoly_eval_sum(st, m, k, (uint32_t)segs, part, out));
+  summed = true;
   return KYB_OK;
 }
 

@@ -87,9 +87,15 @@ k_mul_base64(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ sc
 // the partial points meet through the staging records (the table is the whole LDS) and two additions — wavefronts 0 and 1 side by side, then
 // wavefront 0 — leave the sum in the item's own record, where k_finish* expects it.  Staging: part q of item i in record offset + q n + i
 // (q = 1, 2, 3: the caller provides 4 n records), the result in record offset + i.  Same group element as k_mul_base64, hence the same bytes.
-__device__ __forceinline__ void add_staged_part(ge_p3& h, const uint4* proj, size_t stride, size_t rec) {
+// A staged part is a multiple of B by an ~66-bit piece of a (possibly secret) scalar: the one live lane that reads it zeroes the record
+// behind its load (dead lanes of a ragged last group alias item i0 and may read a cleared record; they never store).
+__device__ __forceinline__ void add_staged_part(ge_p3& h, uint4* proj, size_t stride, size_t rec, bool live) {
   ge_p2 b;
   load_proj_xy(b.X, b.Y, proj, stride, rec); load_proj_z(b.Z, proj, stride, rec);
+  if (live) {
+    const fe z = {{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
+    store_proj(proj, stride, rec, z, z, z);
+  }
   ge_p3 B;
   ge_p2_to_p3(B, b);
   ge_cached c;
@@ -124,12 +130,12 @@ k_mul_base64_quarters(const uint8_t* __restrict__ scalars, const uint8_t* __rest
     if (part >= 2 && live) store_proj(proj, proj_stride, prec + (size_t)(part - 1) * n, h.X, h.Y, h.Z);
     __threadfence_block();
     __syncthreads();
-    if (part < 2) add_staged_part(h, proj, proj_stride, prec + (size_t)(part + 1) * n);      // 0 + 2 | 1 + 3
+    if (part < 2) add_staged_part(h, proj, proj_stride, prec + (size_t)(part + 1) * n, live);      // 0 + 2 | 1 + 3 (and those records cleared)
     if (part == 1 && live) store_proj(proj, proj_stride, prec, h.X, h.Y, h.Z);
     __threadfence_block();
     __syncthreads();
     if (part == 0) {
-      add_staged_part(h, proj, proj_stride, prec);
+      add_staged_part(h, proj, proj_stride, prec, live);
       if (live) store_proj(proj, proj_stride, rec, h.X, h.Y, h.Z);
     }
   }

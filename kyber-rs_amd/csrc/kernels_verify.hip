@@ -363,11 +363,12 @@ hipError_t verify_tail_enc(hipStream_t st, uint4* proj, size_t stride, size_t n,
   hipLaunchKernelGGL(k_verify_fixup, dim3(blocks_for(n)), dim3(KYB_BLOCK), 0, st, sigs, n, flags_a, flavor, status, df);
   return hipGetLastError();
 }
-hipError_t pripoly_eval(hipStream_t st, const uint8_t* coeffs, size_t m, size_t t, const uint32_t* indices, size_t k, uint32_t segs, uint8_t* part, uint8_t* out) {
+hipError_t pripoly_eval_part(hipStream_t st, const uint8_t* coeffs, size_t m, size_t t, const uint32_t* indices, size_t k, uint32_t segs, uint8_t* part, uint8_t* out) {
   const uint32_t len = (uint32_t)((t + segs - 1) / segs);
   hipLaunchKernelGGL(k_pripoly_eval_part, dim3(blocks_for(m * k * segs)), dim3(KYB_BLOCK), 0, st, coeffs, m, t, indices, k, segs, len, segs > 1u ? part : out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || segs == 1u) return e;
+  return hipGetLastError();
+}
+hipError_t pripoly_eval_sum(hipStream_t st, size_t m, size_t k, uint32_t segs, uint8_t* part, uint8_t* out) {
   hipLaunchKernelGGL(k_pripoly_eval_sum, dim3(blocks_for(m * k)), dim3(KYB_BLOCK), 0, st, part, m * k, segs, out);
   return hipGetLastError();
 }

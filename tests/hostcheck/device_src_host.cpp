@@ -498,6 +498,20 @@ void hd_mul_base64_quarters(uint8_t out[32], const uint8_t scalar[32]) {
   ge_encode(w, part[0].X, part[0].Y, part[0].Z);
   memcpy(out, w, 32);
 }
+// the four partial points themselves (encodings, out[32 q ..] = part q): what k_mul_base64_quarters stages between its wavefronts
+void hd_mul_base64_quarter_parts(uint8_t out[128], const uint8_t scalar[32]) {
+  uint8_t whole[32];
+  hd_mul_base64(whole, scalar);          // (builds the table)
+  uint32_t a[8], w[8];
+  load_words(a, scalar);
+  tbl_base64_words tbl{g_base64_table.data()};
+  for (int q = 0; q < 4; ++q) {
+    ge_p3 part;
+    ge_scalarmult_base64_part(part, a, tbl, 11 * q, q == 3 ? KYB_BASE64_POS : 11 * q + 11);
+    ge_encode(w, part.X, part.Y, part.Z);
+    memcpy(out + 32 * q, w, 32);
+  }
+}
 void hd_eddsa_sign(uint8_t sig[64], const uint8_t seed[32], const uint8_t* msg, uint32_t n) {
   ensure_table();
   uint32_t ws[8], x[8], r[8], s[16];

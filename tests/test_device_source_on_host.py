@@ -502,6 +502,26 @@ def test_fixed_base_radix64_matches_oracle(hd, oracle):
     assert hd.hd_overflows() == base
 
 
+def test_quarter_partials_of_the_reference_match_the_device_source(hd, oracle):
+    """the partial points k_mul_base64_quarters stages between its wavefronts, as the secret-hygiene reference computes them
+    (tests/secret_residue.py: sub-scalars of the signed radix-64 digits, times B by the oracle), are the device source's four parts —
+    on the quirk scalars (>= 2^255, top bytes 0x7f .. 0xff), on scalars whose digits fall on a quarter seam, and at random"""
+    import secret_residue as R
+    base = hd.hd_overflows()
+    rnd = random.Random(2064)
+    L = M.L
+    ints = [0, 1, L - 1, L, 2**66 - 1, 2**132, 2**198 - 1, 2**198 + 1, 2**255 - 19, 2**256 - 1]
+    cases = [v.to_bytes(32, "little") for v in ints]
+    for top in (0x7F, 0x80, 0x8F, 0x90, 0xFF):
+        cases += [bytes(rnd.getrandbits(8) for _ in range(31)) + bytes([top]) for _ in range(3)]
+    cases += [bytes(rnd.getrandbits(8) for _ in range(32)) for _ in range(40)]
+    want = R.quarter_points(oracle, np.frombuffer(b"".join(cases), dtype=np.uint8).reshape(-1, 32))
+    for s, w in zip(cases, want):
+        o = B(128); hd.hd_mul_base64_quarter_parts(o, s)
+        assert [o.raw[32 * q:32 * q + 32] for q in range(4)] == [w[q].tobytes() for q in range(4)], s.hex()
+    assert hd.hd_overflows() == base
+
+
 def test_eddsa_sign_golden_lines_device_source(hd):
     """EdDSA::sign (key expansion + deterministic nonce + Schnorr equations) straight from (seed, msg)"""
     for ln in gzip.open(os.path.join(HERE, "golden", "sign.input.gz"), "rt").read().split("\n")[:64]:
