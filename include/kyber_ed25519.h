@@ -12,7 +12,7 @@
  *   enc        32-byte point encoding = `Point::marshal_binary` (point.rs:35-41, ge.rs:112-122).
  *   ext        40 x int32: X[10] Y[10] Z[10] T[10], radix-2^25.5 limbs = `Point.ge`
  *              (`ExtendedGroupElement`, ge.rs:78-83).  Inputs may be any limbs the reference itself
- *              produces (|limb| < 2^29 accepted).  Outputs are the limbs `fe_from_bytes`
+ *              produces (|limb| <= 2^29 - 16 accepted).  Outputs are the limbs `fe_from_bytes`
  *              (fe.rs:67-122) yields for the canonical coordinate value: signed, centred,
  *              |even limb| <= 2^25, |odd limb| <= 2^24 — inside the reference's fe_mul/fe_add input
  *              bounds, so a returned point can be fed straight back into the CPU arithmetic.
@@ -616,12 +616,15 @@ int kyb_diag_wave_stamps(void* dev_buf);
  *     3 page-locked landing area of large pageable results; 4, 5, 6, 7 the engine stream's scratch (projective records, encodings, products of
  *     small linear combinations, pieces of the four-workgroup variable-base product).  Waits for the device first.
  *   kyb_diag_coop(op, a, b, out): one cooperative one-item-per-wavefront primitive on caller-supplied operands (64 words each).
+ *   kyb_diag_fe(op, n, a, b, c, param, out): one field or scalar primitive per item, one item per lane (csrc/selftest_ops.h names the ops):
+ *     a, b, c and out hold 16 words per item (raw limbs, not bytes), param one word per item.  Host pointers.
  *   kyb_diag_phase_stamps(dev_buf): dev_buf = 32 x uint64 of zeroed device memory (NULL = off): the one-item kernels write the constant
  *     100 MHz clock into fixed slots at their phase boundaries (start, scalar multiplication done, partial results combined, inversion
  *     begin / end, stored) — where the time of a one-item call goes (tools/one_item_stamps.py). */
 #ifdef KYB_CROSSCHECK
 int kyb_diag_scratch_read(int which, uint8_t* dst, size_t cap, size_t* bytes);
 int kyb_diag_coop(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+int kyb_diag_fe(int op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* param, uint32_t* out);
 int kyb_diag_phase_stamps(void* dev_buf);
 #endif
 

@@ -721,6 +721,22 @@ int kyb_diag_coop(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
   });
 }
 
+// test hook, not part of the documented ABI: one field / scalar primitive per item on caller-supplied raw limbs (host pointers, 16 words per
+// item in a, b, c and out, one word per item in param; op: selftest_ops.h)
+int kyb_diag_fe(int op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* param, uint32_t* out) {
+  ENTER();
+  if (op < 0 || op >= (int)FE_SELFTEST_OPS) return fail(KYB_E_BAD_ARG, "unknown self-test op");
+  if (n == 0) return KYB_OK;
+  if (!a || !b || !c || !param || !out) return fail(KYB_E_BAD_ARG, "null argument");
+  if (n > (size_t(1) << 24)) return fail(KYB_E_BAD_ARG, "too many items");
+  HostCall hc(g);
+  const int ia = hc.in(a, 64 * n), ib = hc.in(b, 64 * n), ic = hc.in(c, 64 * n), ip = hc.in(param, 4 * n), io = hc.out(out, 64 * n);
+  return hc.run([&](hipStream_t st) {
+    LAUNCHCK(launch::fe_selftest(st, (uint32_t)op, n, hc.dev<uint32_t>(ia), hc.dev<uint32_t>(ib), hc.dev<uint32_t>(ic), hc.dev<uint32_t>(ip), hc.dev<uint32_t>(io)));
+    return KYB_OK;
+  });
+}
+
 // phase stamps of the one-item kernels (kernels_coop.hip KYB_PHASE): dev_buf = 32 x uint64 of device memory, zeroed by the caller; NULL = off
 int kyb_diag_phase_stamps(void* dev_buf) {
   ENTER();

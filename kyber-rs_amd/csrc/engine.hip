@@ -38,6 +38,9 @@
 #include "launch.h"
 #include "scalar_scan.h"
 #include "ge_scalarmult.h"      // table image geometry (KYB_BASE*_TABLE_WORDS, KYB_BT_IDX); plain C++ on the host
+#ifdef KYB_CROSSCHECK
+#include "selftest_ops.h"       // the op count of kyb_diag_fe
+#endif
 #include "host_copy_pool.h"
 
 using namespace kyb;

@@ -502,7 +502,8 @@ KYB_HD uint32_t fe_is_nonzero(const fe& f) {
 }
 
 // Import a reference-layout field element: ten SIGNED int32 limbs, radix 2^25.5 (fe.rs:4-8).
-// Accepts |limb_i| < 2^29 (the reference's own bound is 1.01*2^26): adds 16p limb-wise, then carries.
+// Accepts |limb_i| <= 2^29 - 16 (the reference's own bound is 1.01*2^26): adds 16p limb-wise, then carries.  The bound is 16 p_i of an odd
+// limb (16 (2^25 - 1)): an odd limb below -(2^29 - 16) would wrap.  The cooperative kernels import the same way (cnorm of word + 16p).
 KYB_HD void fe_from_ref10(fe& h, const int32_t s[10]) {
   const uint32_t p4[10] = KYB_FE_4P;
   fe t;

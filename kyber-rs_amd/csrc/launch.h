@@ -1,10 +1,11 @@
 // Host-callable launchers of every kernel group.  The library is built from seven translation units that hipcc
-// compiles in parallel (csrc/Makefile); the CROSS-CHECK build (CROSSCHECK=1, -DKYB_CROSSCHECK: test infrastructure) adds two:
+// compiles in parallel (csrc/Makefile); the CROSS-CHECK build (CROSSCHECK=1, -DKYB_CROSSCHECK: test infrastructure) adds three:
 //
 //   kernels_base.hip      fixed base: table builders, table checksum, k_mul_base64 (the fixed-base kernel)
 //   kernels_ladder.hip    variable base: k_decode_or_identity, k_decode_to_proj, k_mont_prep, k_mul_ladder, k_pair_sum, k_ext_to_proj
 //   [kernels_base_alt.hip  cross-check build only: radix-32 / radix-16 fixed-base kernels and the fused k_sign]
 //   [kernels_window.hip    cross-check build only: windowed variable-base k_mul (mul.algo=0)]
+//   [kernels_selftest.hip  cross-check build only: k_fe_selftest, the per-lane test hook of the field and scalar primitives (selftest_ops.h)]
 //   kernels_verify.hip    SHA-512 users: k_verify_prep / _r / _final, k_sign_hash, k_eddsa_prep
 //   kernels_misc.hip      k_finish, k_encode_batched, k_add, k_equal, k_encode, k_decode, k_poly_eval, k_poly_eval_part
 //   kernels_msm.hip       linear combinations over shared points with PUBLIC scalars: k_msm_tables, k_msm_accumulate (+ k_msm_bases_coop in kernels_coop.hip)
@@ -131,6 +132,9 @@ hipError_t mul_base_coop(hipStream_t st, const uint8_t* sc, size_t n, uint8_t* o
                          DoneFlag df = DoneFlag{}, int waves = 1, bool ext_proj = false);      // waves: 1, or 4 wavefronts per item sharing the 43 windows
 hipError_t coop_selftest(hipStream_t st, int op, const uint32_t* A, const uint32_t* B, uint32_t* out, const uint32_t* table_coop);
 hipError_t diag_phase_stamps(uint64_t* buf);      // (cross-check build only, like coop_selftest)
+// ---- kernels_selftest.hip (cross-check build only) ----
+// n items of 16 words in a, b, c and out, one parameter word each: op = selftest_ops.h fe_selftest_op
+hipError_t fe_selftest(hipStream_t st, uint32_t op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* param, uint32_t* out);
 
 // ---- kernels_verify.hip ----
 hipError_t verify_prep_pts(hipStream_t st, const uint8_t* pub_enc, const int32_t* pubs_ext, const uint8_t* sigs, const uint8_t* msgs, const uint32_t* off, size_t n,

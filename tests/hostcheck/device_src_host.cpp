@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: compiles the DEVICE arithmetic headers (kyber-rs_amd/csrc/*.h) with g++ so
 // that tests/test_device_source_on_host.py can run the exact source the HIP kernels inline — limb
 // bounds included, every multiply shadowed by a 128-bit overflow check — against the oracle on a
-// machine without a GPU.  Built into tests/hostcheck/_build/libdevsrc_host.so by the test itself.
+// machine without a GPU.  Built into tests/hostcheck/_build/libdevsrc_host.so by build() (__graft_entry__.build_devsrc_host; the
+// tests rebuild it when a header is newer), so the GPU tests find it too: they compare k_fe_selftest with hd_fe_selftest below.
 // This library is never loaded by the product (kyber-rs_amd/ loads only libkyber_ed25519_hip.so and
 // fails without a GPU); it is not a CPU fallback.
 #define KYB_HOST_TEST 1
@@ -12,6 +13,7 @@
 #include "../../kyber-rs_amd/csrc/schnorr.h"
 #include "../../kyber-rs_amd/csrc/verify.h"
 #include "../../kyber-rs_amd/csrc/ge_ladder.h"
+#include "../../kyber-rs_amd/csrc/selftest_ops.h"
 
 static std::atomic<long> g_overflows{0};
 extern "C" void kyb_host_overflow(const char*) { g_overflows++; }
@@ -532,5 +534,10 @@ void hd_recode(int8_t e[64], const uint8_t scalar[32]) {
     e[i] = (int8_t)(neg ? -(int)mag : (int)mag);
   }
   e[63] = (int8_t)d.top;
+}
+// the host twin of the cross-check build's k_fe_selftest: the same dispatcher (selftest_ops.h) on the same item layout — 16 words per item in
+// a, b, c and out, one parameter word per item
+void hd_fe_selftest(uint32_t op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* param, uint32_t* out) {
+  for (size_t i = 0; i < n; ++i) fe_selftest_item(op, a + 16 * i, b + 16 * i, c + 16 * i, param[i], out + 16 * i);
 }
 }

@@ -28,7 +28,7 @@ def test_header_and_python_binding_agree():
 def test_test_hooks_are_not_in_the_product_library():
     """round-5 review item 5: fault injection and the scratch reader shipped in the product.  Now the product exports exactly the two
     benchmark diagnostics (the chip's multiply-add rate and the in-kernel clock stamps, which bench.py's roofline needs); the fault
-    injection counters, kyb_diag_scratch_read and kyb_diag_coop exist in the cross-check build only."""
+    injection counters, kyb_diag_scratch_read, kyb_diag_coop and kyb_diag_fe exist in the cross-check build only."""
     import subprocess
     libdir = os.path.join(ROOT, "kyber-rs_amd")
 
@@ -40,7 +40,7 @@ def test_test_hooks_are_not_in_the_product_library():
     assert prod == set(header_symbols()), sorted(prod ^ set(header_symbols()))
     strings = subprocess.run(["strings", "-n", "8", os.path.join(libdir, "libkyber_ed25519_hip.so")], capture_output=True, text=True).stdout
     assert "diag.fail_alloc_after" not in strings and "diag.fail_launch_after" not in strings and "injected launch failure" not in strings
-    assert "k_coop_selftest" not in strings
+    assert "k_coop_selftest" not in strings and "k_fe_selftest" not in strings
     if os.path.exists(os.path.join(libdir, "libkyber_ed25519_hip_crosscheck.so")):
         cross = exported("libkyber_ed25519_hip_crosscheck.so")
         assert cross == prod | set(header_symbols(crosscheck_only=True)), sorted(cross ^ (prod | set(header_symbols(crosscheck_only=True))))

@@ -10,7 +10,6 @@ import hashlib
 import json
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -26,13 +25,8 @@ KATS = json.load(open(os.path.join(HERE, "golden", "kats.json")))
 
 @pytest.fixture(scope="module")
 def hd():
-    src = os.path.join(HERE, "hostcheck", "device_src_host.cpp")
-    out = os.path.join(HERE, "hostcheck", "_build", "libdevsrc_host.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    deps = [src] + [os.path.join(ROOT, "kyber-rs_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "kyber-rs_amd", "csrc")) if f.endswith((".h", ".inc"))]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", out, src])
-    lib = ctypes.CDLL(out)
+    import __graft_entry__
+    lib = ctypes.CDLL(__graft_entry__.build_devsrc_host())          # (rebuilt when a device header is newer)
     lib.hd_overflows.restype = ctypes.c_long
     lib.hd_decode.restype = ctypes.c_int
     return lib
@@ -567,3 +561,55 @@ def test_lincomb_flow_matches_oracle(hd, oracle):
     o = B(32); hd.hd_lincomb(o, b"".join(v.to_bytes(32, "little") for v in lam), p32(ys), t)
     assert o.raw == oracle.mul_base(coeffs[0].to_bytes(32, "little"))
     assert hd.hd_overflows() == base
+
+
+def run_fe_selftest(hd, op, A, B, C, prm):
+    """hd_fe_selftest (the host twin of the cross-check build's k_fe_selftest, selftest_ops.h) on n items of 16 words"""
+    import field_reference as R
+    n = len(A)
+    out = np.zeros((n, 16), np.uint32)
+    hd.hd_fe_selftest.argtypes = [ctypes.c_uint32, ctypes.c_size_t] + [ctypes.c_void_p] * 5
+    arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (A, B, C, prm)]
+    hd.hd_fe_selftest(R.OPS[op], n, *(p32(x) for x in arrs), p32(out))
+    return out
+
+
+def test_field_primitives_at_their_documented_bounds(hd):
+    """every field and scalar primitive of the self-test (selftest_ops.h), run by the overflow-checked C build of the device headers on cases
+    AT its documented input contract (tests/field_reference.py: every limb at k T, one limb at its maximum, carry ripples, special values
+    in loose forms, random limbs inside the bound) == the Python-integer reference, output bounds included, and no 32- or 64-bit overflow
+    anywhere: the contracts fe25519.h states are safe on the C path"""
+    import field_reference as R
+    base = hd.hd_overflows()
+    for op in R.OPS:
+        A, B, C, prm = R.cases(op)
+        out = run_fe_selftest(hd, op, A, B, C, prm)
+        bad = R.check(op, A, B, C, prm, out)
+        assert not bad, bad
+        assert hd.hd_overflows() == base, op
+
+
+def test_reference_layout_import_bound(hd):
+    """fe_from_ref10 (what every kernel that reads `ext` limbs runs, one lane or cooperative) on the documented edge |limb| = 2^29 - 16, limb by
+    limb at both signs, with the reference-layout normal form of a value elsewhere; odd limbs 2^29 - 15 below zero no longer fit the 16p it
+    adds (16 p_odd = 2^29 - 16), which is why the header states this bound and not 2^29"""
+    import field_reference as R
+    m = R.REF10_LIMB_MAX
+    rows = []
+    for v in (0, 1, R.P - 1, R.SQRT_M1, R.D):
+        s = R.ref10_normal(v)
+        for i in range(10):
+            for e in (m, -m):
+                t = list(s); t[i] = e
+                rows.append(t)
+        rows.append([m if i % 2 else -m for i in range(10)])
+        rows.append([-m if i % 2 else m for i in range(10)])
+    A = R._pad(rows)
+    Z = np.zeros_like(A)
+    out = run_fe_selftest(hd, "fe_from_ref10", A, Z, Z, np.zeros(len(A), np.uint32))
+    assert not R.check("fe_from_ref10", A, Z, Z, np.zeros(len(A), np.uint32), out)
+    # one step past the edge: the import is wrong there (this is the reason for the bound, not a contract)
+    t = [0] * 10; t[1] = -(m + 1)
+    A1 = R._pad([t])
+    out = run_fe_selftest(hd, "fe_from_ref10", A1, A1 * 0, A1 * 0, np.zeros(1, np.uint32))
+    assert R.values(out)[0] % R.P != R.value(t) % R.P

@@ -99,6 +99,20 @@ def quad_from_ints(c, vals):
     return q
 
 
+def quad_from_limbs(rows):
+    """four raw limb vectors (ten limbs each, loose limbs allowed) -> quad"""
+    q = np.zeros(64, dtype=np.uint64)
+    for r, limbs in enumerate(rows):
+        for k in range(10):
+            q[16 * r + k] = int(limbs[k])
+    return q
+
+
+def raw_ints_from_quad(q):
+    """the four values sum limb_k 2^POS[k], NOT reduced mod p"""
+    return [sum(int(q[16 * r + k]) << POS[k] for k in range(10)) for r in range(4)]
+
+
 def ints_from_quad(q):
     return [sum(int(q[16 * r + k]) << POS[k] for k in range(10)) % P for r in range(4)]
 
